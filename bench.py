@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fusion-forward samples/sec, 2-modality (tab 1x2000 + img 224x224x3), b=32 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +12,9 @@ collective in the data path ("weak" scaling); timing = barrier + synchronize on 
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-executes itself under `python -m torch.distributed.run`
 (one rank per GPU, 127.0.0.1 rendezvous), so the plain command works as well as the explicit launcher line above.
+
+`--dump-outputs DIR`: rank 0 writes what the last timed step returned -- the logits, (b, 4) float32 -- as DIR/logits.npy.  Model
+and inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
   roofline     : the dominant kernel (split-KV attention core of the image cross-attention), timed with HIP
@@ -676,7 +679,10 @@ def main():
                     help="N > 1: print the line without the training-step record if that record has not returned by then")
     ap.add_argument("--core-precision", choices=["fp32", "bf16", "bf16x3"], default="fp32",
                     help="development switch: bf16 MFMA in the image cross-attention core (the headline is fp32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the logits of the last timed step as DIR/logits.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -745,6 +751,8 @@ def main():
             out = model([tab, img])
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            last_logits = out.detach().float().cpu().numpy()   # host copy now, before the instrumented replay runs the model again
 
         # ---- instrumented replay of the same K steps: HIP events recorded on the launch stream around every
         # launch of the dominant kernel (recording timing events between kernels costs ~1 ms per forward on
@@ -762,6 +770,10 @@ def main():
         barrier()
         elapsed_instrumented = time.perf_counter() - t1
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), last_logits)
 
     if distributed:
         elapsed = hdist.max_over_ranks(elapsed, dev)      # the slowest rank defines the step time

@@ -5,15 +5,20 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
+
+from conftest import assert_close, load_golden
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_prints_one_contract_line():
+def test_bench_prints_one_contract_line(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
-                          "--train-steps", "3"], cwd=ROOT, capture_output=True, text=True, timeout=600, check=True).stdout
+                          "--train-steps", "3", "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600,
+                         check=True).stdout
     lines = [l for l in out.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out
     j = json.loads(lines[0])
@@ -24,6 +29,14 @@ def test_bench_prints_one_contract_line():
     assert j["scaling"] == "weak" and j["vs_baseline"] is None and j["dtype"] == "f32" and j["data"] == "synthetic"
     assert "workload" in j["config"] and "model" not in j["config"]
     assert abs(j["value"] - 32 * 1000.0 / j["ms_per_step"]) <= 1e-3 * j["value"]
+    # --dump-outputs: the logits of the last timed step, on bench.py's seeded inputs -- the reference's own logits on them
+    # (tests/golden/g10_cfg2_b32_bench.npz), as tests/test_gpu_fullsize.py holds the forward to
+    assert sorted(os.listdir(tmp_path)) == ["logits.npy"]
+    got = np.load(tmp_path / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (32, 4)
+    want = load_golden("g10_cfg2_b32_bench")["logits"]
+    for i in range(32):
+        assert_close(torch.from_numpy(got[i]), want[i], rel=1e-3, what=f"dumped logits[{i}]")
     r = j["roofline"]
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and r["peak"] == 157.3
     assert 0.3 < r["frac"] <= 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3

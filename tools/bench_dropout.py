@@ -1,5 +1,5 @@
 import sys, os, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import healnet_amd as hn
 for name, kw, shapes, b in [("cfg2", dict(n_modalities=2, channel_dims=[2000, 3], num_spatial_axes=[1, 2], out_dims=4), [(1, 2000), (224, 224, 3)], 32),
                             ("cfg4", dict(n_modalities=2, channel_dims=[2000, 768], num_spatial_axes=[1, 1], out_dims=4), [(1, 2000), (4096, 768)], 8)]:

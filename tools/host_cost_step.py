@@ -3,8 +3,8 @@
 launches and the Python / autograd path stay) with a cProfile of it, then at the real size with the enqueue time beside the wall
 time.  Round 6: 2.2 ms of host time against 4.06 ms of GPU time per step -- the step is GPU-bound with a 1.8 x margin.
     python tools/host_cost_step.py"""
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import healnet_amd as hn
 from healnet_amd import dist as hdist
 dev = torch.device("cuda", 0)
