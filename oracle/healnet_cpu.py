@@ -109,10 +109,14 @@ def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5) -> Te
 # --------------------------------------------------------------------------------------
 def attention(x: Tensor, context: Optional[Tensor], w_q: Tensor, w_kv: Tensor, w_out: Tensor, b_out: Tensor,
               heads: int, mask: Optional[Tensor] = None, temperature: float = 0.5,
-              return_weights: bool = False, drop_mult: Optional[Tensor] = None):
+              return_weights: bool = False, drop_mult: Optional[Tensor] = None, token_chunk: Optional[int] = None):
     """healnet.py:400-426.  x (b, L, dq) already normalised; context (b, N, D) already normalised
     (or None -> x).  Returns LeakyReLU_{0.01}(concat_heads(P V) W_out^T + b_out) and optionally P
-    with shape (b*heads, L, N) (batch-major head index b*heads + h, :407)."""
+    with shape (b*heads, L, N) (batch-major head index b*heads + h, :407).
+
+    ``token_chunk`` (optional, no weights, no dropout): the same softmax computed over chunks of that many context tokens and
+    merged with running (max, sum) statistics, so that no (b*heads, L, N) score matrix is ever formed -- for very long contexts
+    in fp64.  tests/test_long_context_sensitivity.py pins it to the unchunked path."""
     ctx = x if context is None else context                                         # :404
     b, L, _ = x.shape
     n = ctx.shape[1]
@@ -126,6 +130,10 @@ def attention(x: Tensor, context: Optional[Tensor], w_q: Tensor, w_kv: Tensor, w
         return t.reshape(b, rows, heads, e).permute(0, 2, 1, 3).reshape(b * heads, rows, e)
 
     qh, kh, vh = split(q, L), split(k, n), split(v, n)
+    if token_chunk is not None and not return_weights and drop_mult is None:
+        out = _chunked_softmax_pv(qh, kh, vh, e ** -0.5, temperature, mask, b, heads, token_chunk)
+        out = out.reshape(b, heads, L, e).permute(0, 2, 1, 3).reshape(b, L, inner)
+        return F.leaky_relu(out @ w_out.t() + b_out, negative_slope=1e-2)
     sim = torch.bmm(qh, kh.transpose(1, 2)) * (e ** -0.5)                           # :409
     if mask is not None:                                                            # :411-415
         flat = mask.reshape(b, -1)
@@ -138,6 +146,32 @@ def attention(x: Tensor, context: Optional[Tensor], w_q: Tensor, w_kv: Tensor, w
     out = out.reshape(b, heads, L, e).permute(0, 2, 1, 3).reshape(b, L, inner)      # :425
     out = F.leaky_relu(out @ w_out.t() + b_out, negative_slope=1e-2)                # :383-386, :426
     return (out, attn) if return_weights else out
+
+
+def _chunked_softmax_pv(qh: Tensor, kh: Tensor, vh: Tensor, scale: float, temperature: float, mask: Optional[Tensor],
+                        b: int, heads: int, chunk: int) -> Tensor:
+    """softmax((qh kh^T * scale, masked) / temperature) vh over token chunks, merged by a running max and sum."""
+    bh, L, _ = qh.shape
+    n = kh.shape[1]
+    keep = None
+    if mask is not None:
+        keep = mask.reshape(b, -1)[:, None, None, :].expand(b, heads, 1, n).reshape(bh, 1, n)
+    m = torch.full((bh, L, 1), -math.inf, dtype=qh.dtype, device=qh.device)
+    l = torch.zeros_like(m)
+    acc = torch.zeros(bh, L, vh.shape[-1], dtype=qh.dtype, device=qh.device)
+    for t0 in range(0, n, chunk):
+        s = torch.bmm(qh, kh[:, t0:t0 + chunk].transpose(1, 2)) * scale
+        if keep is not None:
+            s = s.masked_fill(~keep[:, :, t0:t0 + chunk], -torch.finfo(s.dtype).max)
+        s = s / temperature
+        m_new = torch.maximum(m, s.amax(dim=-1, keepdim=True))
+        m_safe = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
+        alpha = torch.exp(m - m_safe)
+        p = torch.exp(s - m_safe)
+        l = l * alpha + p.sum(dim=-1, keepdim=True)
+        acc = acc * alpha + torch.bmm(p, vh[:, t0:t0 + chunk])
+        m = m_new
+    return acc / l
 
 
 # --------------------------------------------------------------------------------------
@@ -158,14 +192,17 @@ def feed_forward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, snn:
 # --------------------------------------------------------------------------------------
 # a9/a10: the fusion loop over a reference-layout state_dict
 # --------------------------------------------------------------------------------------
-def _cross_block(sd: Dict[str, Tensor], pfx: str, x: Tensor, ctx: Tensor, heads: int, mask, keep: Optional[list], dm=None):
+def _cross_block(sd: Dict[str, Tensor], pfx: str, x: Tensor, ctx: Tensor, heads: int, mask, keep: Optional[list], dm=None,
+                 token_chunk: Optional[int] = None):
     xn = layer_norm(x, sd[pfx + "norm.weight"], sd[pfx + "norm.bias"])                                  # :314
     cn = layer_norm(ctx, sd[pfx + "norm_context.weight"], sd[pfx + "norm_context.bias"])              # :316-319
-    y, p = attention(xn, cn, sd[pfx + "fn.to_q.weight"], sd[pfx + "fn.to_kv.weight"],
+    y = attention(xn, cn, sd[pfx + "fn.to_q.weight"], sd[pfx + "fn.to_kv.weight"],
                      sd[pfx + "fn.to_out.0.weight"], sd[pfx + "fn.to_out.0.bias"], heads, mask,
-                     return_weights=True, drop_mult=dm)
-    if keep is not None:
-        keep.append(p)
+                     return_weights=token_chunk is None or keep is not None, drop_mult=dm, token_chunk=token_chunk)
+    if isinstance(y, tuple):
+        y, p = y
+        if keep is not None:
+            keep.append(p)
     return y + x                                                                                         # :236 residual
 
 
@@ -195,7 +232,8 @@ class FusionTrace:
 
 def fusion_forward(sd: Dict[str, Tensor], cfg: FusionConfig, tensors: Sequence[Optional[Tensor]],
                    mask: Optional[Tensor] = None, return_embeddings: bool = False, verbose: bool = False,
-                   trace: Optional[FusionTrace] = None, drop: Optional[Dict[int, Tensor]] = None) -> Tensor:
+                   trace: Optional[FusionTrace] = None, drop: Optional[Dict[int, Tensor]] = None,
+                   token_chunk: Optional[int] = None) -> Tensor:
     """healnet.py:190-250 including its observable quirks:
 
       * ``drop`` (training mode with dropout > 0): {index of the executed block, counted in execution order ->
@@ -209,6 +247,8 @@ def fusion_forward(sd: Dict[str, Tensor], cfg: FusionConfig, tensors: Sequence[O
         reference's ``missing_idx`` (:193) only holds the ``None`` entries INSIDE the list, so a modality beyond a shorter
         list fails in the bare try/except (:238) and still runs its latent self block (fixture g9_verbose_shortlist);
       * ``self_per_cross_attn == 0`` -> no latent blocks; ``>= 2`` is a ValueError in the reference.
+    ``token_chunk``: the cross-attention softmax over chunks of that many tokens (``attention``); ignored by blocks that record
+    their weights (``trace``) or run dropout.
     The bare ``except`` of :238 is NOT restated: real shape errors raise here.
     """
     M = cfg.n_modalities
@@ -240,7 +280,7 @@ def fusion_forward(sd: Dict[str, Tensor], cfg: FusionConfig, tensors: Sequence[O
             if not present[m] and verbose and m < len(tensors):                       # :229-232 (missing_idx, :193)
                 continue
             if present[m]:
-                x = _cross_block(sd, f"layers.{layer}.{2 * m}.", x, ctxs[m], cfg.x_heads, mask, keep, dm(step))
+                x = _cross_block(sd, f"layers.{layer}.{2 * m}.", x, ctxs[m], cfg.x_heads, mask, keep, dm(step), token_chunk)
                 step += 1
                 tags.append((layer, "cross", m))
                 if trace is not None:
