@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -109,14 +109,18 @@ def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5) -> Te
 # --------------------------------------------------------------------------------------
 def attention(x: Tensor, context: Optional[Tensor], w_q: Tensor, w_kv: Tensor, w_out: Tensor, b_out: Tensor,
               heads: int, mask: Optional[Tensor] = None, temperature: float = 0.5,
-              return_weights: bool = False, drop_mult: Optional[Tensor] = None, token_chunk: Optional[int] = None):
+              return_weights: bool = False, drop_mult: Optional[Tensor] = None, token_chunk: Optional[int] = None,
+              tap: Optional[Callable[[str, Tensor], Tensor]] = None):
     """healnet.py:400-426.  x (b, L, dq) already normalised; context (b, N, D) already normalised
     (or None -> x).  Returns LeakyReLU_{0.01}(concat_heads(P V) W_out^T + b_out) and optionally P
     with shape (b*heads, L, N) (batch-major head index b*heads + h, :407).
 
     ``token_chunk`` (optional, no weights, no dropout): the same softmax computed over chunks of that many context tokens and
     merged with running (max, sum) statistics, so that no (b*heads, L, N) score matrix is ever formed -- for very long contexts
-    in fp64.  tests/test_long_context_sensitivity.py pins it to the unchunked path."""
+    in fp64.  tests/test_long_context_sensitivity.py pins it to the unchunked path.
+
+    ``tap`` (optional, test instrumentation): ``tap("attn_pre", t)`` is called with the LeakyReLU input and its result used in
+    its place (see ``fusion_forward``)."""
     ctx = x if context is None else context                                         # :404
     b, L, _ = x.shape
     n = ctx.shape[1]
@@ -133,7 +137,10 @@ def attention(x: Tensor, context: Optional[Tensor], w_q: Tensor, w_kv: Tensor, w
     if token_chunk is not None and not return_weights and drop_mult is None:
         out = _chunked_softmax_pv(qh, kh, vh, e ** -0.5, temperature, mask, b, heads, token_chunk)
         out = out.reshape(b, heads, L, e).permute(0, 2, 1, 3).reshape(b, L, inner)
-        return F.leaky_relu(out @ w_out.t() + b_out, negative_slope=1e-2)
+        pre = out @ w_out.t() + b_out
+        if tap is not None:
+            pre = tap("attn_pre", pre)
+        return F.leaky_relu(pre, negative_slope=1e-2)
     sim = torch.bmm(qh, kh.transpose(1, 2)) * (e ** -0.5)                           # :409
     if mask is not None:                                                            # :411-415
         flat = mask.reshape(b, -1)
@@ -144,7 +151,10 @@ def attention(x: Tensor, context: Optional[Tensor], w_q: Tensor, w_kv: Tensor, w
     pv = attn if drop_mult is None else attn * drop_mult                            # :421 nn.Dropout with a GIVEN mask:
     out = torch.bmm(pv, vh)                                                         # :424   drop_mult = keep / (1 - p)
     out = out.reshape(b, heads, L, e).permute(0, 2, 1, 3).reshape(b, L, inner)      # :425
-    out = F.leaky_relu(out @ w_out.t() + b_out, negative_slope=1e-2)                # :383-386, :426
+    pre = out @ w_out.t() + b_out
+    if tap is not None:
+        pre = tap("attn_pre", pre)
+    out = F.leaky_relu(pre, negative_slope=1e-2)                                    # :383-386, :426
     return (out, attn) if return_weights else out
 
 
@@ -178,13 +188,18 @@ def _chunked_softmax_pv(qh: Tensor, kh: Tensor, vh: Tensor, scale: float, temper
 # a8: gated feed-forward
 # --------------------------------------------------------------------------------------
 def feed_forward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, snn: bool = True,
-                 drop_mult: Optional[Tensor] = None) -> Tensor:
+                 drop_mult: Optional[Tensor] = None, tap: Optional[Callable[[str, Tensor], Tensor]] = None) -> Tensor:
     """healnet.py:339-351 with the SELU (:328-331) or GELU (:323-326) gate; x already normalised.
-    drop_mult: the nn.Dropout of :347 with a given mask (keep / (1 - p), shape of the output)."""
+    drop_mult: the nn.Dropout of :347 with a given mask (keep / (1 - p), shape of the output).
+    tap (optional, test instrumentation): called as tap("gate", g) on the gate input and tap("z", z) on the hidden activation."""
     u = x @ w1.t() + b1
     half = u.shape[-1] // 2
     a, g = u[..., :half], u[..., half:]                                             # chunk(2): value first, gate second
+    if tap is not None:
+        g = tap("gate", g)
     z = a * (F.selu(g) if snn else F.gelu(g))
+    if tap is not None:
+        z = tap("z", z)
     y = z @ w2.t() + b2
     return y if drop_mult is None else y * drop_mult
 
@@ -193,33 +208,40 @@ def feed_forward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, snn:
 # a9/a10: the fusion loop over a reference-layout state_dict
 # --------------------------------------------------------------------------------------
 def _cross_block(sd: Dict[str, Tensor], pfx: str, x: Tensor, ctx: Tensor, heads: int, mask, keep: Optional[list], dm=None,
-                 token_chunk: Optional[int] = None):
+                 token_chunk: Optional[int] = None, tap=None):
     xn = layer_norm(x, sd[pfx + "norm.weight"], sd[pfx + "norm.bias"])                                  # :314
     cn = layer_norm(ctx, sd[pfx + "norm_context.weight"], sd[pfx + "norm_context.bias"])              # :316-319
     y = attention(xn, cn, sd[pfx + "fn.to_q.weight"], sd[pfx + "fn.to_kv.weight"],
                      sd[pfx + "fn.to_out.0.weight"], sd[pfx + "fn.to_out.0.bias"], heads, mask,
-                     return_weights=token_chunk is None or keep is not None, drop_mult=dm, token_chunk=token_chunk)
+                     return_weights=token_chunk is None or keep is not None, drop_mult=dm, token_chunk=token_chunk, tap=tap)
     if isinstance(y, tuple):
         y, p = y
         if keep is not None:
             keep.append(p)
+    if tap is not None:
+        y = tap("out", y)
     return y + x                                                                                         # :236 residual
 
 
-def _self_block(sd: Dict[str, Tensor], pfx: str, x: Tensor, heads: int, keep: Optional[list], dm=None):
+def _self_block(sd: Dict[str, Tensor], pfx: str, x: Tensor, heads: int, keep: Optional[list], dm=None, tap=None):
     xn = layer_norm(x, sd[pfx + "norm.weight"], sd[pfx + "norm.bias"])
     y, p = attention(xn, None, sd[pfx + "fn.to_q.weight"], sd[pfx + "fn.to_kv.weight"],
                      sd[pfx + "fn.to_out.0.weight"], sd[pfx + "fn.to_out.0.bias"], heads, None,
-                     return_weights=True, drop_mult=dm)
+                     return_weights=True, drop_mult=dm, tap=tap)
     if keep is not None:
         keep.append(p)
+    if tap is not None:
+        y = tap("out", y)
     return y + x                                                                                         # :244
 
 
-def _ff_block(sd: Dict[str, Tensor], pfx: str, x: Tensor, snn: bool, dm=None):
+def _ff_block(sd: Dict[str, Tensor], pfx: str, x: Tensor, snn: bool, dm=None, tap=None):
     xn = layer_norm(x, sd[pfx + "norm.weight"], sd[pfx + "norm.bias"])
-    return feed_forward(xn, sd[pfx + "fn.net.0.weight"], sd[pfx + "fn.net.0.bias"],
-                        sd[pfx + "fn.net.2.weight"], sd[pfx + "fn.net.2.bias"], snn, dm) + x             # :237/:245
+    y = feed_forward(xn, sd[pfx + "fn.net.0.weight"], sd[pfx + "fn.net.0.bias"],
+                     sd[pfx + "fn.net.2.weight"], sd[pfx + "fn.net.2.bias"], snn, dm, tap=tap)
+    if tap is not None:
+        y = tap("out", y)
+    return y + x                                                                                         # :237/:245
 
 
 @dataclass
@@ -233,7 +255,7 @@ class FusionTrace:
 def fusion_forward(sd: Dict[str, Tensor], cfg: FusionConfig, tensors: Sequence[Optional[Tensor]],
                    mask: Optional[Tensor] = None, return_embeddings: bool = False, verbose: bool = False,
                    trace: Optional[FusionTrace] = None, drop: Optional[Dict[int, Tensor]] = None,
-                   token_chunk: Optional[int] = None) -> Tensor:
+                   token_chunk: Optional[int] = None, tap: Optional[Callable[[int, str, Tensor], Tensor]] = None) -> Tensor:
     """healnet.py:190-250 including its observable quirks:
 
       * ``drop`` (training mode with dropout > 0): {index of the executed block, counted in execution order ->
@@ -249,6 +271,11 @@ def fusion_forward(sd: Dict[str, Tensor], cfg: FusionConfig, tensors: Sequence[O
       * ``self_per_cross_attn == 0`` -> no latent blocks; ``>= 2`` is a ValueError in the reference.
     ``token_chunk``: the cross-attention softmax over chunks of that many tokens (``attention``); ignored by blocks that record
     their weights (``trace``) or run dropout.
+    ``tap`` (test instrumentation; ``None`` leaves the computation untouched): ``tap(step, site, t)`` is called with the index of
+    the executed block (numbered like ``drop``) and returns the tensor used in place of ``t``.  Sites: ``"attn_pre"`` the
+    LeakyReLU input of an attention block (b, L, d); ``"gate"`` the gate input of a feed-forward block (b, L, 4d); ``"z"`` its
+    hidden activation value * gate(gate input); ``"out"`` the block's residual branch (b, L, d), before ``+ x``.  A tap can
+    record tensors or wrap them in identities with a different backward.
     The bare ``except`` of :238 is NOT restated: real shape errors raise here.
     """
     M = cfg.n_modalities
@@ -275,27 +302,29 @@ def fusion_forward(sd: Dict[str, Tensor], cfg: FusionConfig, tensors: Sequence[O
         raise ValueError("self_per_cross_attn >= 2 fails in the reference (healnet.py:242)")
     step = 0
     dm = (lambda k: None) if drop is None else (lambda k: drop.get(k))
+    tp = (lambda k: None) if tap is None else (lambda k: (lambda site, t: tap(k, site, t)))
     for layer in range(cfg.depth):
         for m in range(M):
             if not present[m] and verbose and m < len(tensors):                       # :229-232 (missing_idx, :193)
                 continue
             if present[m]:
-                x = _cross_block(sd, f"layers.{layer}.{2 * m}.", x, ctxs[m], cfg.x_heads, mask, keep, dm(step), token_chunk)
+                x = _cross_block(sd, f"layers.{layer}.{2 * m}.", x, ctxs[m], cfg.x_heads, mask, keep, dm(step), token_chunk,
+                                 tp(step))
                 step += 1
                 tags.append((layer, "cross", m))
                 if trace is not None:
                     trace.blocks.append(x)
-                x = _ff_block(sd, f"layers.{layer}.{2 * m + 1}.", x, cfg.snn, dm(step))
+                x = _ff_block(sd, f"layers.{layer}.{2 * m + 1}.", x, cfg.snn, dm(step), tp(step))
                 step += 1
                 if trace is not None:
                     trace.blocks.append(x)
             if cfg.self_per_cross_attn > 0:                                           # :241-245
-                x = _self_block(sd, f"layers.{layer}.{2 * M}.0.", x, cfg.l_heads, keep, dm(step))
+                x = _self_block(sd, f"layers.{layer}.{2 * M}.0.", x, cfg.l_heads, keep, dm(step), tp(step))
                 step += 1
                 tags.append((layer, "self", m))
                 if trace is not None:
                     trace.blocks.append(x)
-                x = _ff_block(sd, f"layers.{layer}.{2 * M}.1.", x, cfg.snn, dm(step))
+                x = _ff_block(sd, f"layers.{layer}.{2 * M}.1.", x, cfg.snn, dm(step), tp(step))
                 step += 1
                 if trace is not None:
                     trace.blocks.append(x)
