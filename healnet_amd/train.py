@@ -102,6 +102,9 @@ class FlatParameters:
         ps = [p for p in model.parameters() if p.requires_grad]
         if not ps:
             raise ValueError("model has no trainable parameters")
+        # parameters frozen at flattening stay where they are: no slot, no update -- but calc_reg_loss sums |p| over every
+        # parameter of the model (healnet/utils/train_utils.py:12), so the optimizer still counts them in reg_loss
+        self.outside: List[torch.nn.Parameter] = [p for p in model.parameters() if not p.requires_grad]
         dev = ps[0].device
         _need_gpu(ps[0], "parameters")
         sizes = [(p.numel() + 3) // 4 * 4 for p in ps]            # keep every view 16-byte aligned
@@ -174,6 +177,11 @@ class FlatParameters:
         such gradients are copied into their slot and re-pointed; a re-allocated parameter (``model.to(...)``,
         ``load_state_dict(assign=True)``) cannot be repaired silently and raises."""
         base_p, base_g = self.params.data_ptr(), self.grads.data_ptr()
+        for p in self.outside:
+            if p.requires_grad:
+                raise RuntimeError("healnet_amd: a parameter that was frozen when flatten_parameters ran has been unfrozen since; it has "
+                                   "no slot in the flat buffer and would never be updated -- call flatten_parameters(model) again and "
+                                   "rebuild the optimizer")
         for p, off in zip(self.views, self.offsets):
             if p.data_ptr() != base_p + 4 * off:
                 raise RuntimeError("healnet_amd: a parameter no longer lives in the flat buffer (model.to(...) / assign-loading after "
@@ -196,7 +204,13 @@ class FusedL1Adam(torch.optim.Optimizer):
     ``calc_reg_loss`` (healnet/utils/train_utils.py:5-14) folded in: ``step()`` is ONE pass over the flat buffers --
     gradient of l1 * sum |p|, Adam moments, update, and the reg_loss value itself (``.reg_loss``, a 0-dim device tensor
     holding l1 * sum |p| of the parameters the forward just used).  ``param_groups[0]['lr']`` / ``['betas']`` are read
-    at every step, so torch's OneCycleLR (which cycles both) drives it unchanged."""
+    at every step, so torch's OneCycleLR (which cycles both) drives it unchanged.
+
+    Frozen parameters (``requires_grad_(False)`` after ``flatten_parameters``) are skipped as ``torch.optim.Adam`` skips a
+    parameter whose ``.grad`` is None: parameter and moments stay untouched and its own update count stands still (kept as
+    ``state['view_skips']``, one count per view, only once something was frozen).  While every view is trainable and all
+    counts agree the step is one launch over the whole buffer; otherwise one launch per run of adjacent trainable views
+    with the same count (views are 16-byte aligned, so every run is), and reg_loss comes from one separate reduction."""
 
     def __init__(self, flat: FlatParameters, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, l1: float = 0.0,
                  grad_scale: float = 1.0):
@@ -235,6 +249,29 @@ class FusedL1Adam(torch.optim.Optimizer):
     def zero_grad(self, set_to_none: bool = False) -> None:   # gradients stay views of the flat buffer
         self.flat.zero_grad()
 
+    def _runs(self, st: dict):
+        """-> ([(first float, floats, update count)] of the runs to launch, the per-view skip counts after this step or None when
+        nothing has ever been frozen).  ``st['step']`` already counts this step."""
+        f = self.flat
+        train = [p.requires_grad for p in f.views]
+        skips = st.get("view_skips")
+        if skips is None:
+            if all(train):
+                return [(0, f.numel, int(st["step"]))], None
+            skips = [0] * len(f.views)
+        skips = [int(k) + (0 if t else 1) for k, t in zip(skips, train)]
+        ends = f.offsets[1:] + [f.numel]
+        runs: List[Tuple[int, int, int]] = []
+        for i, t in enumerate(train):
+            if not t:
+                continue
+            step = int(st["step"]) - skips[i]
+            if runs and runs[-1][0] + runs[-1][1] == f.offsets[i] and runs[-1][2] == step:
+                runs[-1] = (runs[-1][0], ends[i] - runs[-1][0], step)
+            else:
+                runs.append((f.offsets[i], ends[i] - f.offsets[i], step))
+        return runs, skips
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -246,12 +283,30 @@ class FusedL1Adam(torch.optim.Optimizer):
         st["step"] = int(st["step"]) + 1
         f = self.flat
         f.relink()
+        runs, skips = self._runs(st)
         try:
-            _capi.check(_capi.lib().hn_l1_adam_step(f.params.data_ptr(), f.grads.data_ptr(), st["exp_avg"].data_ptr(),
-                                                    st["exp_avg_sq"].data_ptr(), f.numel, float(g["l1"]), float(g["grad_scale"]),
-                                                    float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                                    st["step"], self.reg_loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                    _stream(f.params.device)), "hn_l1_adam_step")
+            lib, stream = _capi.lib(), _stream(f.params.device)
+
+            def launch(start, n, step, reg):
+                _capi.check(lib.hn_l1_adam_step(f.params.data_ptr() + 4 * start, f.grads.data_ptr() + 4 * start,
+                                                st["exp_avg"].data_ptr() + 4 * start, st["exp_avg_sq"].data_ptr() + 4 * start, n,
+                                                float(g["l1"]), float(g["grad_scale"]), float(g["lr"]), float(g["betas"][0]),
+                                                float(g["betas"][1]), float(g["eps"]), step, reg, self._ws.data_ptr(), self._ws.numel(),
+                                                stream), "hn_l1_adam_step")
+            if len(runs) == 1 and runs[0][:2] == (0, f.numel):     # every view trainable, one update count: the single fused pass
+                launch(0, f.numel, runs[0][2], self.reg_loss.data_ptr())
+                if f.outside:
+                    self.reg_loss.add_(torch.stack([p.detach().abs().sum() for p in f.outside]).sum(), alpha=float(g["l1"]))
+            else:
+                # |p| of the parameters BEFORE the update, frozen ones included, then the runs
+                total = f.params.abs().sum()
+                if f.outside:
+                    total = total + torch.stack([p.detach().abs().sum() for p in f.outside]).sum()
+                torch.mul(total, float(g["l1"]), out=self.reg_loss)
+                for start, n, step in runs:
+                    launch(start, n, step, None)
+            if skips is not None:
+                st["view_skips"] = skips
         except _capi.CoresidencyLost as err:
             # a cluster-mode chain of THIS step (or of one the host had run ahead of) lost an exchange: the gradients may carry NaN.
             # The update is skipped -- on the device an already enqueued hn_l1_adam_step does the same by itself -- and the count

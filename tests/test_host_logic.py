@@ -223,6 +223,67 @@ def test_fused_adam_state_is_checkpointed():
         assert opt2._steps == 7 and float(opt2.exp_avg.sum()) == 4.0 and opt2.exp_avg.shape == (8,)
 
 
+def _cpu_flat(shapes, outside=()):
+    """A FlatParameters laid out on the host (the class refuses host tensors; its layout logic does not need a device)."""
+    import healnet_amd as hn
+    f = hn.train.FlatParameters.__new__(hn.train.FlatParameters)
+    sizes = [(int(torch.tensor(s).prod()) + 3) // 4 * 4 for s in shapes]
+    f.numel = sum(sizes)
+    f.params, f.grads = torch.zeros(f.numel), torch.zeros(f.numel)
+    f.views, f.offsets, f.outside = [], [], list(outside)
+    off = 0
+    for s, n in zip(shapes, sizes):
+        k = int(torch.tensor(s).prod())
+        p = torch.nn.Parameter(f.params[off:off + k].view(s))
+        p.grad = f.grads[off:off + k].view(s)
+        f.views.append(p)
+        f.offsets.append(off)
+        off += n
+    return f
+
+
+def test_fused_adam_launch_plan_with_frozen_parameters():
+    """one hn_l1_adam_step over the whole buffer per step while every view is trainable; with a view frozen
+    after flattening, one launch per run of trainable views (16-byte aligned starts, the frozen slot never swept), reg_loss from a
+    separate reduction (the launches get NULL), and per-view update counts so a view that sat out resumes with its own count;
+    a parameter frozen before flattening counts in reg_loss and unfreezing it raises."""
+    import unittest.mock as mock
+    import healnet_amd as hn
+    frozen_out = torch.nn.Parameter(torch.full((3,), -2.0), requires_grad=False)
+    f = _cpu_flat([(2, 3), (5,), (4,), (3, 3)], outside=[frozen_out])
+    f.params.copy_(torch.arange(f.numel, dtype=torch.float32) - 10)
+    with mock.patch.object(hn.train._capi, "lib") as lib, mock.patch.object(hn.train, "_stream", return_value=0):
+        lib.return_value.hn_l1_adam_workspace_bytes.return_value = 256
+        lib.return_value.hn_l1_adam_step.return_value = 0
+        call = lib.return_value.hn_l1_adam_step
+        opt = hn.train.FusedL1Adam(f, lr=1e-3, l1=0.5)
+        base = f.params.data_ptr()
+
+        def launches():
+            out = [((c.args[0] - base) // 4, c.args[4], c.args[11], c.args[12]) for c in call.call_args_list]
+            call.reset_mock()
+            return out
+        for step in (1, 2):
+            opt.step()
+            got = launches()
+            assert len(got) == 1 and got[0][:3] == (0, f.numel, step) and got[0][3] == opt.reg_loss.data_ptr()
+        assert "view_skips" not in opt.state[f.views[0]]
+        f.views[1].requires_grad_(False)                      # frozen after flattening: slot [8, 16)
+        for step in (3, 4):
+            opt.step()
+            assert launches() == [(0, 8, step, None), (16, 16, step, None)]
+            assert float(opt.reg_loss) == pytest.approx(0.5 * (float(f.params.abs().sum()) + 6.0))
+        f.views[1].requires_grad_(True)                       # resumes with its own count (2 updates so far, this is its 3rd)
+        opt.step()
+        assert launches() == [(0, 8, 5, None), (8, 8, 3, None), (16, 16, 5, None)]
+        assert opt.state[f.views[0]]["view_skips"] == [0, 2, 0, 0]
+        assert all(f.offsets[i] % 4 == 0 for i in range(4))
+        frozen_out.requires_grad_(True)                       # frozen before flattening, unfrozen since: it has no slot
+        with pytest.raises(RuntimeError, match="flatten_parameters"):
+            opt.step()
+        assert not call.called
+
+
 def test_non_fp32_parameters_are_refused():
     """model.half() / .bfloat16() / .double() would make the kernels read the wrong bytes: the descriptor refuses."""
     model = HealNet(n_modalities=1, channel_dims=[3], num_spatial_axes=[2], out_dims=2, depth=1, l_c=4, l_d=8, x_heads=1,
